@@ -12,11 +12,15 @@ generates its own range: presharded), one RCCL all-gather of the halo catalogue 
 per snapshot inside the timed step; --scaling weak (1e8 per GPU, default) or strong
 (1e8 in total, configs[3]).
 
-Prints ONE JSON line on rank 0 (contract in the task statement): value =
-particle-snapshots/s over all ranks; roofline = algorithmic bytes of the oa_step
-kernel / its HIP-event duration vs 8 TB/s; cpu_baseline = the CPU oracle (NumPy
-restatement of the reference path, 1 core) timed on a bounded sample of the same
-workload, with its apsis IDs checked against the GPU's for that sample.
+Prints ONE JSON line on rank 0: value = particle-snapshots/s over all ranks,
+ms_per_step = the wall time of one timed step.  A plain run sets up, warms up, times
+the K steps and prints that line.  --dump-outputs DIR also writes what the last timed
+step computed (dump_outputs) as DIR/<name>.npy.  --full adds the figures that take
+runs of their own: roofline = algorithmic bytes of the oa_step kernel / its HIP-event
+duration vs 8 TB/s (each step is re-run for its record count); the records' fetch
+time; N > 1: the output-stage pass; cpu_baseline = the CPU oracle (NumPy restatement
+of the reference path) timed on a bounded sample of the same workload, with its apsis
+IDs checked against the GPU's for that sample.
 """
 import argparse
 import json
@@ -103,6 +107,61 @@ def cpu_baseline(snap_cur, snap_prev, cat_cur, cat_prev, H, z, gpu_prev_angles,
     return out
 
 
+DUMP_SAMPLE = 1 << 20       # rows of a sampled output (dump_outputs)
+DUMP_NONFINITE = -2.0       # written for a NaN or infinite angle or r-hat component
+
+
+def _finite(a):
+    """``a`` with DUMP_NONFINITE where it is not finite: an angle is an arccos sum (>= 0)
+    and r-hat a unit vector, so the value stands for nothing else; the reference's
+    arithmetic gives NaN for a few particles (a cosine rounded past 1, r = 0), and a NaN
+    compares unequal to itself."""
+    return np.where(np.isfinite(a), a, a.dtype.type(DUMP_NONFINITE))
+
+
+def _sample_rows(n, seed):
+    """Sorted, fixed rows of an n-row output: all of them up to DUMP_SAMPLE."""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(seed).integers(0, n, DUMP_SAMPLE))
+
+
+def dump_outputs(outdir, records, last, write):
+    """--dump-outputs: what the last timed step handed its caller, as float arrays.
+
+    ``records``: the step's fetched (offsets, apsis IDs, f16 angles) -- offsets whole,
+    IDs and angles at one seeded sample of the records.  ``last``: its PreparedStep,
+    whose r-hat and state words (f16 angle | sign << 16) are the state the next snapshot
+    reads, at a seeded sample of the particles (none where large halos keep theirs in
+    bucket order).  Every value written is finite (_finite).  A sampled row costs 8 B + 4 B of a record and 12 B (f64: 24 B) + 4 B
+    + 4 B of the state: 42 MB at most, and the offsets.  ``write``: this rank writes the
+    files."""
+    import torch
+    offsets, ids, ang = records
+    out = {}
+    if write:
+        rows = _sample_rows(len(ids), 1)
+        out = {'apsis_offsets': np.asarray(offsets, dtype=np.float64),
+               'apsis_ids': np.asarray(ids)[rows].astype(np.float64),
+               'apsis_angles': _finite(np.asarray(ang)[rows].astype(np.float32))}
+    if write and last.buckets is None and last.rhat is not None:
+        rows = _sample_rows(last.n, 2)
+        d_rows = torch.from_numpy(rows).to(last.meta.device)
+        rhat = last.rhat.view(-1, 3)[d_rows].cpu().numpy()
+        meta = last.meta[d_rows].cpu().numpy().view(np.uint32)
+        out['state_rhat'] = _finite(rhat.astype(np.float64 if rhat.dtype == np.float64
+                                               else np.float32))
+        out['state_angles'] = _finite((meta & 0xFFFF).astype(np.uint16).view(np.float16)
+                                      .astype(np.float32))
+        out['state_sign'] = ((meta >> 16) & 1).astype(np.float32)
+    if write:
+        os.makedirs(outdir, exist_ok=True)
+        for name, a in out.items():
+            np.save(os.path.join(outdir, name + '.npy'), a)
+        log('dumped %s (%.1f MB) to %s' % (', '.join(sorted(out)),
+                                           sum(a.nbytes for a in out.values()) / 1e6, outdir))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -114,12 +173,20 @@ def main():
     ap.add_argument('--dtype', default='float32', choices=['float32', 'float64'],
                     help='coordinates / velocities / catalogue dtype (configs[1] is float64)')
     ap.add_argument('--max-snapshots', type=int, default=40,
-                    help='device memory guard: snapshots generated (steps + warmup + 1)')
+                    help='device memory guard: at most this many snapshots are generated '
+                         '(steps + warmup + 1 of them; a longer run repeats its timed steps)')
     ap.add_argument('--cpu-halos', type=int, default=1500)
     ap.add_argument('--cpu-workers', type=int, default=0,
                     help='processes of the P-core CPU baseline (0: min(16, cpu_count): the '
                          'GPU box gives one GPU 16 host cores)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: the roofline (each timed '
+                         'step re-run for its record count), the records\' fetch time, the '
+                         'CPU baseline and, N > 1, the output-stage pass')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy '
+                         '(dump_outputs)')
     ap.add_argument('--scaling', default=None, choices=['weak', 'strong'],
                     help='strong (default for N > 1): --particles in total over the ranks, '
                          'BASELINE configs[3]; weak: --particles per GPU (configs[2] on every '
@@ -173,7 +240,7 @@ def main():
 
     import orbitanalysis_amd  # noqa: F401
     from orbitanalysis_amd import _native
-    from orbitanalysis_amd.engine import OrbitEngine, SnapshotState, layout_of, meta_angles
+    from orbitanalysis_amd.engine import N_WS, OrbitEngine, SnapshotState, layout_of, meta_angles
     from orbitanalysis_amd.synthetic_device import DevicePlummer
     from orbitanalysis_amd.utils import hubble_parameter
 
@@ -183,11 +250,24 @@ def main():
     per_rank = int(args.particles) if args.scaling == 'weak' else int(args.particles) // world
     gen = DevicePlummer(n_halos=args.halos, n_particles=per_rank, seed=0,
                         rank=rank, world=world, device=dev, dtype=args.dtype)
-    # one snapshot per step, none reused: every timed pair is (s - 1, s) of one orbit
-    S = args.steps + args.warmup + 1
-    if S > args.max_snapshots:
-        raise SystemExit('--steps + --warmup + 1 = %d snapshots > --max-snapshots %d'
-                         % (S, args.max_snapshots))
+    # one snapshot per step, every timed pair (s - 1, s) of one orbit, none reused up to
+    # --max-snapshots; a longer run goes round its D distinct timed steps again (timed
+    # step i is step i mod D: as in the clock ramp, a step launched again reads the state
+    # its predecessor left in its own buffers and writes the same outputs)
+    S = min(args.steps + args.warmup + 1, args.max_snapshots)
+    D = S - 1 - args.warmup
+    if D < 1:
+        raise SystemExit('--warmup + 2 = %d snapshots > --max-snapshots %d'
+                         % (args.warmup + 2, args.max_snapshots))
+    if shard and args.steps > D >= N_WS:
+        # the sharded engine's steps rotate through N_WS workspaces in launch order: a whole
+        # number of rotations per round, so a step never meets its two predecessors' records
+        D -= D % N_WS
+        S = args.warmup + D + 1
+
+    def tk(i):
+        """Timed step i's place among the prepared steps."""
+        return args.warmup + i % D
     snaps, cats = [], []
     for s in range(S):
         snaps.append(gen.snapshot(s))
@@ -206,7 +286,7 @@ def main():
         eng.launch(prep0, None)
         chain = [(prep0, 0)]
         layout = layout_of(prep0, exists)
-        for t in range(1, args.warmup + args.steps + 1):
+        for t in range(1, S):
             tp = time.perf_counter()
             pr = eng.prepare(snaps[t], cats[t][0], cats[t][2], H, z, exists, True,
                              prev_layout=layout)
@@ -224,7 +304,7 @@ def main():
         sp0 = seng.prepare(snaps[0], cats[0][0], cats[0][2], H, z, exists, False)
         seng.launch(sp0)
         chain = [(sp0, 0)]
-        for t in range(1, args.warmup + args.steps + 1):
+        for t in range(1, S):
             tp = time.perf_counter()
             chain.append((seng.prepare(snaps[t], cats[t][0], cats[t][2], H, z, exists, True,
                                        prev=chain[-1][0]), t))
@@ -266,14 +346,14 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        last_res = run(args.warmup + i, evs[i])
+        last_res = run(tk(i), evs[i])
     t_issue = time.perf_counter() - t0          # the host's launch calls of the K steps
     torch.cuda.synchronize()
     if dist:
         barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    units = sum(preps[args.warmup + i].n for i in range(args.steps))
+    units = sum(preps[tk(i)].n for i in range(args.steps))
     if dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -285,51 +365,61 @@ def main():
     if status:
         raise RuntimeError('oa_step reported status %#x (table overflow) during the bench' % status)
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
-    last = preps[-1]
+    last = preps[tk(args.steps - 1)]          # the last timed step
     n_apsis = int(ws.total.item())
+    fdt = np.dtype(str(snaps[0]['ids'].dtype).replace('torch.', ''))
+    log('elapsed %.4f s for %d steps; k_step %.3f ms; apsis %d'
+        % (elapsed, args.steps, kern_ms, n_apsis))
 
-    # the records' gather to rank 0 and D2H of the last timed step (outside the timed
-    # region, as the driver overlaps it with the next snapshot's step): ms per fetch,
-    # the max over ranks, over 3 repetitions
-    fetch = []
-    fdt = snaps[0]['ids'].cpu().numpy().dtype
-    for _ in range(3):
-        if dist:
-            barrier()
-        torch.cuda.synchronize()
-        tf = time.perf_counter()
-        (seng if shard else eng).fetch_async(last_res, fdt).wait()
-        if dist:
-            barrier()
-        fetch.append(time.perf_counter() - tf)
-    fetch_ms = float(np.median(fetch)) * 1e3
-    if dist:
-        t = torch.tensor([fetch_ms], dtype=torch.float64, device=cdev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        fetch_ms = float(t.item())
+    if args.dump_outputs:
+        # the last timed step's records, fetched as a caller would (N > 1: gathered to
+        # rank 0, so every rank takes part), before anything below runs a step again
+        rec = (seng if shard else eng).fetch_async(last_res, fdt).wait()
+        dump_outputs(args.dump_outputs, rec, last, rank == 0)
 
-    # each timed step's own apsis count (its records' bytes): the steps are re-run
-    # once, untimed, in order (each reads the state its predecessor wrote); N > 1: this
-    # rank's own count (the roofline is rank 0's kernel)
+    # --full: the records' gather to rank 0 and D2H of the last timed step (outside the
+    # timed region, as the driver overlaps it with the next snapshot's step): ms per
+    # fetch, the max over ranks, over 3 repetitions
+    fetch_ms = None
+    if args.full:
+        fetch = []
+        for _ in range(3):
+            if dist:
+                barrier()
+            torch.cuda.synchronize()
+            tf = time.perf_counter()
+            (seng if shard else eng).fetch_async(last_res, fdt).wait()
+            if dist:
+                barrier()
+            fetch.append(time.perf_counter() - tf)
+        fetch_ms = float(np.median(fetch)) * 1e3
+        if dist:
+            t = torch.tensor([fetch_ms], dtype=torch.float64, device=cdev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            fetch_ms = float(t.item())
+
+    # --full: each timed step's own apsis count (its records' bytes): the steps are
+    # re-run once, untimed, in order (each reads the state its predecessor wrote); N > 1:
+    # this rank's own count (the roofline is rank 0's kernel)
     n_aps = []
-    for i in range(args.steps):
-        r_i = run(args.warmup + i)
+    for i in range(args.steps if args.full else 0):
+        r_i = run(tk(i))
         torch.cuda.synchronize()
         n_aps.append(int(ws.total.item()) if not shard else int(r_i.lp.res.total.item()))
 
-    # N > 1: the same K steps again with the output stage of the drop-in driver
+    # --full, N > 1: the same K steps again with the output stage of the drop-in driver
     # (track_orbits' pipelined order: step s launched, then the records of s - 1 start
     # towards the host, then those of s - 2 are waited for), every rank storing its own
     # records into the shared host buffer (host_share.SharedRecordStage); timed as the
     # compute pass.  value stays the compute pass (as at N = 1, where the records' D2H is
     # outside the timed region too); this pass is reported beside it.
     stage = None
-    if world > 1 and not args.no_output_stage:
+    if args.full and world > 1 and not args.no_output_stage:
         from orbitanalysis_amd.host_share import SharedRecordStage
         seng._stage = SharedRecordStage(seng.group, seng.rank, seng.world, seng.ROOT, timeout=120)
         if not seng._stage.probe(eng.lib, cdev, True):
             stage = {'skipped': 'a rank could not page-lock a shared-memory segment'}
-    if world > 1 and not args.no_output_stage and stage is None:
+    if args.full and world > 1 and not args.no_output_stage and stage is None:
         seng.profile_fetch = False
         pend, moved = [], []
         for i in range(2):                        # warm: maps and registers the slots
@@ -340,7 +430,7 @@ def main():
         t1 = time.perf_counter()
         prev_res = None
         for i in range(args.steps):
-            r_i = run(args.warmup + i, defer=True)
+            r_i = run(tk(i), defer=True)
             if prev_res is not None:
                 pend.append(seng.fetch_async(prev_res, fdt))
             if len(pend) > 1:
@@ -372,36 +462,47 @@ def main():
         log('output stage: %.3f ms per step (compute only %.3f); bytes stored per rank %s'
             % (stage['e2e_ms_per_step'], elapsed / args.steps * 1e3,
                stage['bytes_stored_per_step_by_rank']))
-    bytes_launch = float(np.mean([step_bytes(preps[args.warmup + i], preps[args.warmup + i].n_prev,
-                                             n_aps[i]) for i in range(args.steps)]))
-    achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
-    log('elapsed %.4f s for %d steps; k_step %.3f ms; %.1f GB/s; apsis %d'
-        % (elapsed, args.steps, kern_ms, achieved, n_apsis))
-
-    traffic, counters = None, None
-    for name in ('pmc_k_step.json', 'pmc_part.json'):
-        pmc = os.path.join(ROOT, 'profiles', name)
-        if traffic is not None or not os.path.exists(pmc):
-            continue
-        with open(pmc) as f:
-            pj = json.load(f)
-        # only for the workload the counters were collected on
-        if (pj.get('particles'), pj.get('halos'), pj.get('n_gpus', 1)) == \
-                (per_rank, args.halos, 1):
-            traffic = pj.get('hbm_bytes_per_launch')
-            counters = {'source': 'profiles/' + name,
-                        'fetch_size_bytes': pj.get('fetch_size_bytes'),
-                        'write_size_bytes': pj.get('write_size_bytes'),
-                        'width_calibration': pj.get('width_calibration'),
-                        'traffic_over_algorithmic': traffic / bytes_launch if traffic else None}
-    # §8(d): read-only bytes against the peak (the reads alone, per launch)
-    read_launch = float(np.mean([step_bytes(preps[args.warmup + i], preps[args.warmup + i].n_prev,
-                                            0, reads_only=True) for i in range(args.steps)]))
+    roofline = None
+    if args.full:
+        bytes_launch = float(np.mean([step_bytes(preps[tk(i)],
+                                                 preps[tk(i)].n_prev, n_aps[i])
+                                      for i in range(args.steps)]))
+        achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
+        log('roofline: %.1f GB/s by algorithmic bytes' % achieved)
+        traffic, counters = None, None
+        for name in ('pmc_k_step.json', 'pmc_part.json'):
+            pmc = os.path.join(ROOT, 'profiles', name)
+            if traffic is not None or not os.path.exists(pmc):
+                continue
+            with open(pmc) as f:
+                pj = json.load(f)
+            # only for the workload the counters were collected on
+            if (pj.get('particles'), pj.get('halos'), pj.get('n_gpus', 1)) == \
+                    (per_rank, args.halos, 1):
+                traffic = pj.get('hbm_bytes_per_launch')
+                counters = {'source': 'profiles/' + name,
+                            'fetch_size_bytes': pj.get('fetch_size_bytes'),
+                            'write_size_bytes': pj.get('write_size_bytes'),
+                            'width_calibration': pj.get('width_calibration'),
+                            'traffic_over_algorithmic': traffic / bytes_launch
+                            if traffic else None}
+        # §8(d): read-only bytes against the peak (the reads alone, per launch)
+        read_launch = float(np.mean([step_bytes(preps[tk(i)],
+                                                preps[tk(i)].n_prev, 0,
+                                                reads_only=True) for i in range(args.steps)]))
+        roofline = {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS,
+                    'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
+                    'traffic': traffic, 'kernel': kernel_label(last), 'kernel_ms': kern_ms,
+                    'alg_bytes_per_launch': bytes_launch,
+                    'alg_read_bytes_per_launch': read_launch,
+                    'read_only_achieved': read_launch / (kern_ms * 1e-3) / 1e9,
+                    'read_only_frac': read_launch / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                    'counters': counters}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        pr_last, s_last = chain[-1]
-        prev_pr, s_prev = chain[-2]
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        pr_last, s_last = chain[tk(args.steps - 1) + 1]
+        prev_pr, s_prev = chain[tk(args.steps - 1)]
         ang_prev = meta_angles(prev_pr.meta)
         offs = ws.offsets[:int(last.has_prog.sum()) + 1].cpu().numpy()
         gids = ws.out_ids[:n_apsis].cpu().numpy()
@@ -439,7 +540,7 @@ def main():
                            'the same warm-up steps (GPU clock ramp after the host-side '
                            'setup); the timed region is exactly the K steps' % ramp,
             'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
-            'scaling': args.scaling, 'vs_baseline': None,
+            'scaling': args.scaling, 'vs_baseline': None, 'full': args.full,
             'dtype': last.plan.coord.name.replace('float', 'f'),
             'data': 'synthetic: %d Plummer spheres (device-generated, AHW sampling, leapfrog '
                     'orbits), region cut r<4a, per-snapshot shuffled blocks, int64 randperm IDs'
@@ -453,6 +554,7 @@ def main():
                                       args.halos, last.plan.coord.name.replace('float', 'f'),
                                       args.mode),
                        'particles_per_step_per_gpu': int(last.n),
+                       'distinct_timed_steps': D,
                        'halos': args.halos, 'work_items': int(last.n_small),
                        'large_halos': int(last.n_global),
                        'parallelism': 'id-range shards x%d (ShardedEngine, presharded; one '
@@ -475,14 +577,7 @@ def main():
                        'weak_scaling_config': 'bench.py --scaling weak: configs[2] (1e8 '
                                               'particles) on every rank'
                                               if world > 1 else None},
-            'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS,
-                         'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
-                         'traffic': traffic, 'kernel': kernel_label(last), 'kernel_ms': kern_ms,
-                         'alg_bytes_per_launch': bytes_launch,
-                         'alg_read_bytes_per_launch': read_launch,
-                         'read_only_achieved': read_launch / (kern_ms * 1e-3) / 1e9,
-                         'read_only_frac': read_launch / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         'counters': counters},
+            'roofline': roofline,
             'cpu_baseline': cpu,
         }
         print(json.dumps(out), flush=True)

@@ -7,7 +7,7 @@ if [ "${SKIP_TESTS:-0}" = 0 ]; then
 fi
 for rep in ${REPS:-1 2}; do
   for v in ${PJV:-1 0}; do
-    ORBIT_PJOIN=$v timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} \
+    ORBIT_PJOIN=$v timeout -k 10 300 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline ${BENCH_ARGS:-} \
       > $O/ab_${T}_${v}_$rep.json 2> $O/ab_${T}_${v}_$rep.err
     rc=$?; echo "pj=$v rep$rep $(grep -o 'k_step [0-9.]* ms' $O/ab_${T}_${v}_$rep.err) $(grep -o '"ms_per_step": [0-9.]*' $O/ab_${T}_${v}_$rep.json)"; [ $rc = 0 ] || exit $rc
   done

@@ -8,7 +8,7 @@
 # steps:
 #   tests     python -m pytest tests -m gpu ($TESTS selects files / -k, default all)
 #   smoke     __graft_entry__.smoke()
-#   bench     bench.py $BENCH_ARGS (default workload, CPU baseline included)
+#   bench     bench.py --full $BENCH_ARGS (default workload, roofline and CPU baseline included)
 #   prof      rocprofv3 --kernel-trace --stats over bench.py --steps 10
 #   pmc       FETCH_SIZE / WRITE_SIZE passes over k_step -> pmc_k_step_$TAG.json
 #   big       configs[1] (1e7 f64, 100 large halos) bench + rocprof
@@ -40,10 +40,10 @@ smoke)
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke_$T.log" 2>&1
   rc=$?; tail -2 "$O/smoke_$T.log"; ok $rc smoke ;;
 bench)
-  timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > "$O/bench_$T.json" 2> "$O/bench_$T.err"
+  timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > "$O/bench_$T.json" 2> "$O/bench_$T.err"
   rc=$?; tail -3 "$O/bench_$T.err"; cat "$O/bench_$T.json"; ok $rc bench ;;
 prof)
-  prof "$O/prof_$T" 400 "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} \
+  prof "$O/prof_$T" 400 "$R/bench.py" --steps 10 --warmup 3 --full --no-cpu-baseline ${BENCH_ARGS:-} \
     > "$O/bench_prof_$T.json" 2> "$O/bench_prof_$T.err"
   rc=$?; python3 tools/kstats.py "$O/prof_$T" | head -8
   python3 tools/trace_window.py "$O/prof_$T" ${RAMP:-30} ${WARM:-5} ${STEPS_T:-20} "$O/trace_window_$T.json"; ok $rc prof ;;
@@ -54,13 +54,13 @@ pmc)
   python3 tools/pmc_summary.py "$O/pmc_$T" "${N0:-99998874}" "$O/pmc_k_step_$T.json"; ok $? pmc_summary ;;
 big)
   prof "$O/prof_big_$T" 400 "$R/bench.py" --dtype float64 --particles 1e7 --halos 100 \
-    --steps 10 --warmup 3 --no-cpu-baseline > "$O/big_$T.json" 2> "$O/big_$T.err"
+    --steps 10 --warmup 3 --full --no-cpu-baseline > "$O/big_$T.json" 2> "$O/big_$T.err"
   rc=$?; cat "$O/big_$T.json"; python3 tools/kstats.py "$O/prof_big_$T"; ok $rc big ;;
 envsweep)
   # bench.py $BENCH_ARGS under environment settings ($ENVS: space-separated NAME=VALUE,NAME=VALUE)
   for rep in ${REPS:-1 2}; do
     for e in ${ENVS:-ORBIT_DIRECT=1}; do
-      env ${e//,/ } timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline \
+      env ${e//,/ } timeout -k 10 300 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline \
         ${BENCH_ARGS:-} > "$O/es_${T}_${e}_$rep.json" 2> "$O/es_${T}_${e}_$rep.err"
       rc=$?; echo "$e rep$rep $(grep -o 'k_step [0-9.]* ms' "$O/es_${T}_${e}_$rep.err") $(grep -o '"ms_per_step": [0-9.]*' "$O/es_${T}_${e}_$rep.json")"; ok $rc "envsweep $e"
     done
@@ -84,7 +84,7 @@ bigsweep)
   for rep in ${REPS:-1 2}; do
     for e in ${BIG_ENVS:-ORBIT_PART_ENTRIES=4096}; do
       env ${e//,/ } timeout -k 10 300 python bench.py --dtype float64 --particles 1e7 --halos 100 \
-        --steps 10 --warmup 3 --no-cpu-baseline > "$O/bs_${T}_${e}_$rep.json" 2> "$O/bs_${T}_${e}_$rep.err"
+        --steps 10 --warmup 3 --full --no-cpu-baseline > "$O/bs_${T}_${e}_$rep.json" 2> "$O/bs_${T}_${e}_$rep.err"
       rc=$?; echo "$e rep$rep $(grep -o 'k_step [0-9.]* ms' "$O/bs_${T}_${e}_$rep.err")"; ok $rc "bigsweep $e"
     done
   done ;;
@@ -118,14 +118,14 @@ b2)
   # production run has one process per GPU); the rehearsal checks the plumbing
   ORBIT_DIRECT=${B2_DIRECT:-0} timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
     --master-addr 127.0.0.1 --master-port ${B2_PORT:-29517} bench.py --gpus 2 --steps 5 --warmup 2 \
-    --backend gloo --scaling "$sc" --no-cpu-baseline ${B2_ARGS:-} > "$O/b2_${sc}_$T.json" 2> "$O/b2_${sc}_$T.err"
+    --backend gloo --scaling "$sc" --full --no-cpu-baseline ${B2_ARGS:-} > "$O/b2_${sc}_$T.json" 2> "$O/b2_${sc}_$T.err"
   rc=$?; grep -v Warning "$O/b2_${sc}_$T.err" | tail -3; cat "$O/b2_${sc}_$T.json"; ok $rc b2 ;;
 ab)
   D=$R/nbody-orbit-analysis_amd/variants
   for rep in ${REPS:-1 2}; do
     for v in ${VARS:-base}; do
       lib=""; [ "$v" != base ] && lib="$D/lib_$v.so"
-      ORBIT_HIP_LIB=$lib timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline \
+      ORBIT_HIP_LIB=$lib timeout -k 10 300 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline \
         ${BENCH_ARGS:-} > "$O/ab_${T}_${v}_$rep.json" 2> "$O/ab_${T}_${v}_$rep.err"
       rc=$?; echo "$v rep$rep $(grep -o 'k_step [0-9.]* ms' "$O/ab_${T}_${v}_$rep.err") \
 $(grep -o '"ms_per_step": [0-9.]*\|"kernel_ms": [0-9.]*' "$O/ab_${T}_${v}_$rep.json" | tr '\n' ' ')"; ok $rc "ab $v"

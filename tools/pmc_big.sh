@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 for k in ${KERNELS:-k_part_join k_part_scatter k_gather_recs}; do
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -k 10 120 rocprofv3 --pmc $c --kernel-include-regex "$k" --output-format csv \
-      -d "$O/${k}_$c" -o run -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline \
+      -d "$O/${k}_$c" -o run -- python3 "$R/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline \
       --dtype float64 --particles 1e7 --halos 100 > "$O/${k}_$c.out" 2> "$O/${k}_$c.err"
     rc=$?; echo "$k $c rc=$rc"; case $rc in 0) ;; *) exit $rc;; esac
   done

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in $VARIANTS; do
   lib=$R/nbody-orbit-analysis_amd/variants/lib_$v.so; [ "$v" = base ] && lib=$R/nbody-orbit-analysis_amd/liborbit_hip.so
   ORBIT_HIP_LIB=$lib timeout -k 10 300 rocprofv3 --pmc $COUNTERS --kernel-include-regex 'k_step' --output-format csv \
-      -d "$O/$v" -o run -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline > "$O/$v.out" 2> "$O/$v.err"
+      -d "$O/$v" -o run -- python3 "$R/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline > "$O/$v.out" 2> "$O/$v.err"
   rc=$?; echo "$v rc=$rc"
   case $rc in 124|134|137|139) echo FATAL; exit $rc;; esac
 done
