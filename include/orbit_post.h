@@ -50,6 +50,8 @@ extern "C" {
 #define OA_POST_OVERFLOW 4u     /* oa_main_progenitors: a block's halo tally overflowed  */
 #define OA_POST_BOUNDS 8u       /* oa_collate_step: a computed position fell outside its
                                    halo's range (inconsistent workspace); nothing stored  */
+#define OA_POST_UNSORTED 16u    /* oa_decompose: a collated slice is not strictly increasing;
+                                   that block's outputs are left zero                      */
 
 /* One round of collate_apsides for one snapshot: merge the kept apsis IDs of every
  * collated halo into its cumulative sorted-unique (key, count) state. */
@@ -93,7 +95,7 @@ typedef struct oa_collate_args {
 int oa_collate_step(const oa_collate_args *args, void *stream);
 
 /* sizeof() of this header's ABI structs (0 oa_collate_args, 1 oa_central_args,
- * 2 oa_mainprog_args) so a binding can verify its layout; -1 otherwise. */
+ * 2 oa_mainprog_args, 3 oa_decomp_args) so a binding can verify its layout; -1 otherwise. */
 int64_t oa_post_struct_size(int32_t which);
 
 /* Convert order keys back to IDs of `out_kind` (n elements). */
@@ -146,6 +148,59 @@ typedef struct oa_mainprog_args {
 
 int64_t oa_mainprog_workspace_bytes(int64_t n_halo_pids, int64_t n_tracked);
 int oa_main_progenitors(const oa_mainprog_args *args, void *stream);
+
+/* Orbiting / infalling decomposition of a snapshot against the collated state: per
+ * particle of region block b its collated orbit count (0 when its ID is not in block b's
+ * slice), radius and radial velocity about the block's centre in float64 arithmetic, and
+ * per block the radial number / mass profiles by count class.
+ *
+ * A block longer than OA_DECOMP_SHARE particles is split over several work-groups, each
+ * adding its LDS histogram to the block's row. */
+#define OA_DECOMP_SHARE 16384
+#define OA_DECOMP_MAX_CELLS 4096   /* n_bins * n_classes */
+#define OA_DECOMP_MAX_KEYS 4096    /* largest lds_keys */
+
+typedef struct oa_decomp_args {
+    const void *ids;            /* (N,) particle IDs of id_kind                            */
+    const void *coords;         /* (N,3) AoS, float32 or float64                           */
+    const void *vels;           /* (N,3) AoS, float32 or float64                           */
+    const void *masses;         /* (N,) float32 or float64, or NULL (scalar mass: the
+                                   caller scales `number`)                                 */
+    int64_t n;                  /* particles                                               */
+    int32_t id_kind;
+    int32_t coord_f64, vel_f64, mass_f64;
+    int32_t n_blocks;
+    int32_t n_box_dims;         /* 0 (no box) or 3                                         */
+    const int64_t *offsets;     /* [n_blocks + 1] block bounds, non-decreasing in [0, N]   */
+    const double *centres;      /* (n_blocks,3)                                            */
+    const double *bulk;         /* (n_blocks,3)                                            */
+    const double *radii;        /* (n_blocks,)                                             */
+    double box[3];              /* L per dim                                               */
+    double half[3];             /* L / 2 per dim                                           */
+    double hubble_over_1pz;     /* H(z) / (1 + z); 0: no Hubble term                       */
+    const uint64_t *col_keys;   /* collated IDs as order keys (signed kinds: value ^ 2^63),
+                                   strictly increasing within each slice                   */
+    const int64_t *col_cnt;     /* their orbit counts                                      */
+    const int64_t *col_off;     /* [n_blocks + 1] slice bounds in col_keys                 */
+    int64_t n_col;              /* collated entries                                        */
+    const double *r_edges;      /* [n_bins + 1] strictly increasing                        */
+    int32_t n_bins;             /* >= 1                                                    */
+    int32_t n_classes;          /* >= 2; n_bins * n_classes <= OA_DECOMP_MAX_CELLS          */
+    int32_t scaled;             /* bin r / radius (1) or r (0)                             */
+    int32_t lds_keys;           /* slice entries held in LDS at once: a power of two in
+                                   [64, OA_DECOMP_MAX_KEYS]; longer slices stream through
+                                   in tiles of this size                                   */
+    int32_t *count;             /* out [N]; only elements inside a block are written       */
+    void *r;                    /* out [N] float32 if coords and vels are, else float64    */
+    void *vr;                   /* out [N] likewise (NaN at r == 0)                        */
+    int64_t *number;            /* out [n_blocks, n_classes, n_bins], zeroed by the call   */
+    double *mass;               /* out likewise; required when masses is given             */
+    int32_t *status;            /* OR-ed OA_POST_UNSORTED (that block: outputs zero) or
+                                   OA_POST_BOUNDS (block or slice bounds outside their
+                                   arrays: nothing computed for that block)                */
+} oa_decomp_args;
+
+int oa_decompose(const oa_decomp_args *args, void *stream);
 
 /* Diagnostic builds only (-DOA_STAMPS=1): k_central's per-block phase timestamps of its
  * last launch (8 per block, s_memrealtime at 100 MHz).  Returns the number of values

@@ -13,7 +13,7 @@ import numpy as np
 PKG = os.path.dirname(os.path.abspath(__file__))
 # ORBIT_HIP_LIB selects an alternative build (kernel variants for tuning sweeps)
 LIB_PATH = os.environ.get('ORBIT_HIP_LIB') or os.path.join(PKG, 'liborbit_hip.so')
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 c_i32, c_i64, c_dbl, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
 
@@ -107,11 +107,25 @@ class MainProgArgs(ctypes.Structure):
                 ('status', c_vp)]
 
 
+class DecompArgs(ctypes.Structure):
+    _fields_ = [('ids', c_vp), ('coords', c_vp), ('vels', c_vp), ('masses', c_vp), ('n', c_i64),
+                ('id_kind', c_i32), ('coord_f64', c_i32), ('vel_f64', c_i32), ('mass_f64', c_i32),
+                ('n_blocks', c_i32), ('n_box_dims', c_i32), ('offsets', c_vp), ('centres', c_vp),
+                ('bulk', c_vp), ('radii', c_vp), ('box', c_dbl * 3), ('half', c_dbl * 3),
+                ('hubble_over_1pz', c_dbl), ('col_keys', c_vp), ('col_cnt', c_vp),
+                ('col_off', c_vp), ('n_col', c_i64), ('r_edges', c_vp), ('n_bins', c_i32),
+                ('n_classes', c_i32), ('scaled', c_i32), ('lds_keys', c_i32), ('count', c_vp),
+                ('r', c_vp), ('vr', c_vp), ('number', c_vp), ('mass', c_vp), ('status', c_vp)]
+
+
 # include/orbit_post.h constants
 ID_KIND = {np.dtype('int64'): 0, np.dtype('uint64'): 1, np.dtype('int32'): 2, np.dtype('uint32'): 3}
 COLLATE_CHUNK = 4096
 CENTRAL_MAX_N = 4096
-POST_MISSING, POST_SENTINEL, POST_OVERFLOW, POST_BOUNDS = 1, 2, 4, 8
+POST_MISSING, POST_SENTINEL, POST_OVERFLOW, POST_BOUNDS, POST_UNSORTED = 1, 2, 4, 8, 16
+DECOMP_SHARE = 16384            # particles of a block per work-group (oa_decompose)
+DECOMP_MAX_CELLS = 4096
+DECOMP_MAX_KEYS = 4096
 
 # every symbol include/orbit_hip.h and include/orbit_post.h declare: name -> (restype, argtypes)
 SYMBOLS = {
@@ -153,6 +167,7 @@ SYMBOLS = {
     'oa_central_ids': (ctypes.c_int, [ctypes.POINTER(CentralArgs), c_vp]),
     'oa_mainprog_workspace_bytes': (c_i64, [c_i64, c_i64]),
     'oa_main_progenitors': (ctypes.c_int, [ctypes.POINTER(MainProgArgs), c_vp]),
+    'oa_decompose': (ctypes.c_int, [ctypes.POINTER(DecompArgs), c_vp]),
 }
 
 
@@ -191,7 +206,7 @@ def load(require_device=False):
                 raise NativeUnavailable('ABI struct %d size mismatch: C %d, Python %d'
                                         % (k, lib.oa_struct_size(k), v))
         post = {0: ctypes.sizeof(CollateArgs), 1: ctypes.sizeof(CentralArgs),
-                2: ctypes.sizeof(MainProgArgs)}
+                2: ctypes.sizeof(MainProgArgs), 3: ctypes.sizeof(DecompArgs)}
         for k, v in post.items():
             if lib.oa_post_struct_size(k) != v:
                 raise NativeUnavailable('ABI post struct %d size mismatch: C %d, Python %d'

@@ -9,6 +9,8 @@
 //   get_central_particle_ids       progenitors.py:38-56       -> k_central
 //   find_main_progenitors          progenitors.py:82-117      -> k_mp_insert,
 //                                  k_mp_probe, k_mp_lookup, k_mp_tally
+// and, with no reference code (its example script's last step), the orbiting / infalling
+// decomposition of a snapshot against the collated state       -> k_decompose
 //
 // Design: no global sort anywhere.
 //  * collate keeps, per collated halo, the cumulative sorted-unique (ID, count) list
@@ -28,6 +30,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <math.h>
+#include <type_traits>
 
 #include "orbit_hip.h"
 #include "orbit_post.h"
@@ -1154,6 +1157,323 @@ __global__ __launch_bounds__(256) void k_mp_tally(const oa_mainprog_args a, cons
         a.result[b] = best ? (int64_t)(0xFFFFFFFFull - (best & 0xFFFFFFFFull)) : -1;
 }
 
+// ------------------------------------------------------------------ decomposition
+// A snapshot joined against the collated state (no reference code: the contract is
+// include/orbit_post.h and tests/decomp_oracle.py).  Work item w = b + g is the part of
+// region block b inside the g-th run of DSHARE particles of the snapshot: b + off[b] /
+// DSHARE is strictly increasing in b, so a work-group finds its block by a binary search
+// over the offsets and a block longer than DSHARE spreads over several work-groups.  The
+// block's collated slice is staged in LDS (keys and counts; checked strictly increasing
+// as it is staged) and the particles stream past it, DU per thread per trip, a trip's
+// loads all issued together (the first trip's before the staging); a slice
+// longer than lds_keys streams through LDS in tiles and a wave searches a tile only when
+// one of its keys lies in the tile's key range, which costs every trip a pass over the
+// slice: meant for slices of a few lds_keys.  r, v_r and the count go out coalesced; the
+// profiles accumulate in LDS and are added to the block's row once per work-group.
+// Measured at 1e8 particles (profiles/bench_post_decompose.jsonl): the LDS binary search
+// beats an LDS hash index (which costs a third more LDS, so fewer work-groups per CU), and
+// 512 threads x 2 particles beats wider trips and a software prefetch of the next trip.
+#ifndef OA_DECOMP_T
+#define OA_DECOMP_T 512         // k_decompose: threads per work-group
+#endif
+#ifndef OA_DECOMP_U
+#define OA_DECOMP_U 2           // particles per thread per trip
+#endif
+#ifndef OA_DECOMP_HASH
+#define OA_DECOMP_HASH 0        // 1 (measurement only): a slice that fits LDS is joined through
+#endif                          //    an LDS hash index of its keys instead of the binary search
+constexpr int DT = OA_DECOMP_T, DU = OA_DECOMP_U;
+constexpr int DSHARE = OA_DECOMP_SHARE;
+static_assert((DSHARE & (DSHARE - 1)) == 0 && DSHARE % (DT * DU) == 0, "share: whole trips");
+
+// streamed-once coordinates and velocities: non-temporal (aux bit 1), the slice and the
+// offsets keep L2
+template <typename TX>
+__device__ __forceinline__ void load_xyz_nt(i32x4 r, uint32_t vo, uint32_t so, TX (&x)[3]) {
+    if constexpr (sizeof(TX) == 4) {
+        const f32x3 v = pb_v3f32(r, (int32_t)vo, (int32_t)so, 2);
+        x[0] = v.x; x[1] = v.y; x[2] = v.z;
+    } else {
+        const f64x2 v = pb_v2f64(r, (int32_t)vo, (int32_t)so, 2);
+        x[0] = v.x; x[1] = v.y; x[2] = pb_f64(r, (int32_t)(vo + 16u), (int32_t)so, 2);
+    }
+}
+
+// tile [t0, t0 + nt) of the slice at cb into LDS, then the strictly-increasing check of
+// its keys (the first against the key before the tile); barriers inside
+__device__ __forceinline__ void decomp_stage(const oa_decomp_args &a, int64_t cb, int64_t t0,
+                                             int nt, uint64_t *tk, int *tc, int *s_bad) {
+    for (int i = threadIdx.x; i < nt; i += DT) {
+        const int64_t c = a.col_cnt[cb + t0 + i];
+        tk[i] = a.col_keys[cb + t0 + i];
+        tc[i] = c < 0 ? 0 : (c > 0x7FFFFFFFll ? 0x7FFFFFFF : (int)c);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nt; i += DT) {
+        if (i == 0 && t0 == 0) continue;
+        const uint64_t prev = i ? tk[i - 1] : a.col_keys[cb + t0 - 1];
+        if (!(tk[i] > prev)) *s_bad = 1;
+    }
+    __syncthreads();
+}
+
+// DU keys against the nt >= 1 sorted keys in LDS, the searches interleaved (one trip
+// count for all): base ends at the last key <= the particle's, if any
+__device__ __forceinline__ void decomp_search(const uint64_t *tk, const int *tc, int nt,
+                                              const uint64_t (&key)[DU], int (&cnt)[DU]) {
+    int base[DU];
+#pragma unroll
+    for (int u = 0; u < DU; ++u) base[u] = 0;
+    for (int n = nt; n > 1;) {
+        const int half = n >> 1;
+#pragma unroll
+        for (int u = 0; u < DU; ++u)
+            if (tk[base[u] + half] <= key[u]) base[u] += half;
+        n -= half;
+    }
+#pragma unroll
+    for (int u = 0; u < DU; ++u)
+        if (tk[base[u]] == key[u]) cnt[u] = tc[base[u]];
+}
+
+#if OA_DECOMP_HASH
+// Hash index of the staged slice: 2 S 16-bit slots holding positions in tk (0xFFFF:
+// free), open addressing, multiplicative hash (the top bits of key * 2^64 / phi).
+__device__ __forceinline__ uint32_t decomp_hash(uint64_t key, int shift) {
+    return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> shift);
+}
+__device__ __forceinline__ void decomp_hash_build(const uint64_t *tk, int nt, uint16_t *ht, int S) {
+    uint32_t *hw = reinterpret_cast<uint32_t *>(ht);
+    for (int i = threadIdx.x; i < S; i += DT) hw[i] = 0xFFFFFFFFu;
+    __syncthreads();
+    const uint32_t mask = 2u * (uint32_t)S - 1u;
+    const int shift = 64 - (32 - __clz(2 * S - 1));
+    for (int i = threadIdx.x; i < nt; i += DT) {
+        uint32_t h = decomp_hash(tk[i], shift) & mask;
+        for (;;) {
+            uint32_t *w = hw + (h >> 1);
+            const int sh = (h & 1u) * 16;
+            uint32_t old = *w;
+            bool placed = false;
+            while (((old >> sh) & 0xFFFFu) == 0xFFFFu) {
+                const uint32_t want = (old & ~(0xFFFFu << sh)) | ((uint32_t)i << sh);
+                const uint32_t prev = atomicCAS(w, old, want);
+                if (prev == old) { placed = true; break; }
+                old = prev;
+            }
+            if (placed) break;
+            h = (h + 1u) & mask;
+        }
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ void decomp_probe(const uint64_t *tk, const int *tc, const uint16_t *ht,
+                                             int S, const uint64_t (&key)[DU], int (&cnt)[DU]) {
+    const uint32_t mask = 2u * (uint32_t)S - 1u;
+    const int shift = 64 - (32 - __clz(2 * S - 1));
+    uint32_t h[DU];
+    bool open[DU];
+#pragma unroll
+    for (int u = 0; u < DU; ++u) { h[u] = decomp_hash(key[u], shift) & mask; open[u] = true; }
+    for (bool any = true; any;) {
+        any = false;
+#pragma unroll
+        for (int u = 0; u < DU; ++u) {
+            if (!open[u]) continue;
+            const uint32_t idx = ht[h[u]];
+            if (idx == 0xFFFFu) { open[u] = false; continue; }
+            if (tk[idx] == key[u]) { cnt[u] = tc[idx]; open[u] = false; continue; }
+            h[u] = (h[u] + 1u) & mask;
+            any = true;
+        }
+    }
+}
+#endif
+
+template <typename TO>
+__device__ __forceinline__ void decomp_zero(const oa_decomp_args &a, int64_t p0, int np) {
+    for (int i = threadIdx.x; i < np; i += DT) {
+        a.count[p0 + i] = 0;
+        static_cast<TO *>(a.r)[p0 + i] = (TO)0;
+        static_cast<TO *>(a.vr)[p0 + i] = (TO)0;
+    }
+}
+
+// LDS (S = a.lds_keys, E = a.n_bins, C = E * a.n_classes): [S] u64 keys, [E + 1] f64 edges,
+// [C] f64 mass cells, [S] int counts, [C] int number cells
+template <int KIND, typename TX, typename TV>
+__global__ __launch_bounds__(DT) void k_decompose(const oa_decomp_args a) {
+    using TO = typename std::conditional<sizeof(TX) == 4 && sizeof(TV) == 4, float, double>::type;
+    extern __shared__ __attribute__((aligned(16))) char dc_smem[];
+    __shared__ int s_bad;
+    const int S = a.lds_keys, E = a.n_bins, C = E * a.n_classes;
+    uint64_t *tk = reinterpret_cast<uint64_t *>(dc_smem);
+    double *ed = reinterpret_cast<double *>(tk + S);
+    double *hm = ed + E + 1;
+    int *tc = reinterpret_cast<int *>(hm + C);
+    int *hn = tc + S;
+#if OA_DECOMP_HASH
+    uint16_t *ht = reinterpret_cast<uint16_t *>(hn + C);    // [2 S]
+#endif
+    const int tid = threadIdx.x;
+    // the block of this work item: the largest b with b + off[b] / DSHARE <= w
+    const int64_t w = blockIdx.x;
+    if (a.offsets[0] / DSHARE > w) return;
+    int lo = 0, hi = a.n_blocks;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (mid + a.offsets[mid] / DSHARE <= w) lo = mid; else hi = mid;
+    }
+    const int b = lo;
+    const int64_t g = w - b;
+    const int64_t s = a.offsets[b], e = a.offsets[b + 1];
+    if (s < 0 || e < s || e > a.n) {                         // nothing of it can be addressed
+        if (tid == 0 && a.status) atomicOr(a.status, (int32_t)OA_POST_BOUNDS);
+        return;
+    }
+    const int64_t p0 = s > g * DSHARE ? s : g * DSHARE;
+    const int64_t p1 = e < (g + 1) * DSHARE ? e : (g + 1) * DSHARE;
+    if (p0 >= p1) return;
+    const int np = (int)(p1 - p0);                           // <= DSHARE
+    const int64_t cb = a.col_off[b], ce = a.col_off[b + 1];
+    const bool bad_slice = cb < 0 || ce < cb || ce > a.n_col;
+    const int64_t L = bad_slice ? 0 : ce - cb;
+    for (int i = tid; i < C; i += DT) { hn[i] = 0; hm[i] = 0.0; }
+    for (int i = tid; i <= E; i += DT) ed[i] = a.r_edges[i];
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
+    constexpr int SG = (KIND == OA_ID_I64 || KIND == OA_ID_I32) ? 1 : 0;
+    const TX *x = static_cast<const TX *>(a.coords);
+    const TV *v = static_cast<const TV *>(a.vels);
+    const i32x4 rx = post_rsrc(x + 3 * p0, (uint32_t)np * 3u * (uint32_t)sizeof(TX));
+    const i32x4 rv = post_rsrc(v + 3 * p0, (uint32_t)np * 3u * (uint32_t)sizeof(TV));
+    const uint32_t vox = (uint32_t)tid * 3u * (uint32_t)sizeof(TX);
+    const uint32_t vov = (uint32_t)tid * 3u * (uint32_t)sizeof(TV);
+    // the loads of one trip (DU particles per thread, DT apart).  Past-the-piece lanes: the
+    // ID and mass index is clamped, the buffer loads read 0
+    auto issue = [&](int i0, uint64_t (&key)[DU], TX (&xs)[DU][3], TV (&vs)[DU][3], double (&ms)[DU]) {
+#pragma unroll
+        for (int u = 0; u < DU; ++u) {
+            const int i = i0 + u * DT + tid;
+            key[u] = to_key(load_val_nt<KIND>(a.ids, p0 + (i < np ? i : np - 1)), SG);
+            load_xyz_nt<TX>(rx, vox, (uint32_t)(i0 + u * DT) * 3u * (uint32_t)sizeof(TX), xs[u]);
+            load_xyz_nt<TV>(rv, vov, (uint32_t)(i0 + u * DT) * 3u * (uint32_t)sizeof(TV), vs[u]);
+            ms[u] = 0.0;
+        }
+        if (a.masses)
+#pragma unroll
+            for (int u = 0; u < DU; ++u) {
+                const int i = i0 + u * DT + tid;
+                const int64_t p = p0 + (i < np ? i : np - 1);
+                ms[u] = a.mass_f64 ? __builtin_nontemporal_load(static_cast<const double *>(a.masses) + p)
+                                   : (double)__builtin_nontemporal_load(static_cast<const float *>(a.masses) + p);
+            }
+    };
+    uint64_t key[DU];
+    TX xs[DU][3];
+    TV vs[DU][3];
+    double ms[DU];
+    issue(0, key, xs, vs, ms);                               // in flight while the slice is staged
+    const bool single = L <= S;                              // the whole slice is one tile
+    if (single && L > 0) decomp_stage(a, cb, 0, (int)L, tk, tc, &s_bad);
+    if (bad_slice || s_bad) {
+        decomp_zero<TO>(a, p0, np);
+        if (tid == 0 && a.status)
+            atomicOr(a.status, (int32_t)(bad_slice ? OA_POST_BOUNDS : OA_POST_UNSORTED));
+        return;
+    }
+#if OA_DECOMP_HASH
+    if (single && L > 0) decomp_hash_build(tk, (int)L, ht, S);
+#endif
+    const double c0 = a.centres[3 * (int64_t)b], c1 = a.centres[3 * (int64_t)b + 1],
+                 c2 = a.centres[3 * (int64_t)b + 2];
+    const double u0 = a.bulk[3 * (int64_t)b], u1 = a.bulk[3 * (int64_t)b + 1],
+                 u2 = a.bulk[3 * (int64_t)b + 2];
+    const double R = a.radii[b], hz = a.hubble_over_1pz;
+    for (int i0 = 0; i0 < np; i0 += DT * DU) {
+        const int i1 = i0 + DT * DU;
+        int cnt[DU];
+#pragma unroll
+        for (int u = 0; u < DU; ++u) cnt[u] = 0;
+        if (single) {
+#if OA_DECOMP_HASH
+            if (L > 0) decomp_probe(tk, tc, ht, S, key, cnt);
+#else
+            if (L > 0) decomp_search(tk, tc, (int)L, key, cnt);
+#endif
+        } else {
+            uint64_t prev_last = 0;
+            for (int64_t t0 = 0; t0 < L; t0 += S) {
+                const int nt = L - t0 < S ? (int)(L - t0) : S;
+                decomp_stage(a, cb, t0, nt, tk, tc, &s_bad);
+                const uint64_t last = tk[nt - 1];
+                bool in = false;
+#pragma unroll
+                for (int u = 0; u < DU; ++u) in |= key[u] <= last && (t0 == 0 || key[u] > prev_last);
+                if (__any(in)) {
+                    int c[DU];
+#pragma unroll
+                    for (int u = 0; u < DU; ++u) c[u] = -1;
+                    decomp_search(tk, tc, nt, key, c);
+#pragma unroll
+                    for (int u = 0; u < DU; ++u) if (c[u] >= 0) cnt[u] = c[u];
+                }
+                prev_last = last;
+                __syncthreads();                             // the tile is free again
+            }
+            if (s_bad) {                                     // uniform: read after a barrier
+                decomp_zero<TO>(a, p0, np);
+                if (tid == 0 && a.status) atomicOr(a.status, (int32_t)OA_POST_UNSORTED);
+                return;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < DU; ++u) {
+            const int i = i0 + u * DT + tid;
+            if (i >= np) continue;
+            double d[3] = {(double)xs[u][0] - c0, (double)xs[u][1] - c1, (double)xs[u][2] - c2};
+            for (int k = 0; k < a.n_box_dims; ++k) {
+                if (d[k] > a.half[k]) d[k] -= a.box[k];
+                if (d[k] < -a.half[k]) d[k] += a.box[k];
+            }
+            const double r = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+            double w0 = (double)vs[u][0] - u0, w1 = (double)vs[u][1] - u1, w2 = (double)vs[u][2] - u2;
+            if (hz != 0.0) { w0 += hz * d[0]; w1 += hz * d[1]; w2 += hz * d[2]; }
+            const double vr = ((w0 * d[0] + w1 * d[1]) + w2 * d[2]) / r;
+            a.count[p0 + i] = cnt[u];
+            static_cast<TO *>(a.r)[p0 + i] = (TO)r;
+            static_cast<TO *>(a.vr)[p0 + i] = (TO)vr;
+            const double t = a.scaled ? r / R : r;
+            if (t >= ed[0] && t < ed[E]) {                   // NaN fails both
+                int kb = 0;                                  // the last edge <= t, in [0, E)
+                for (int n = E; n > 1;) {
+                    const int half = n >> 1;
+                    if (ed[kb + half] <= t) kb += half;
+                    n -= half;
+                }
+                const int q = cnt[u] < a.n_classes - 1 ? cnt[u] : a.n_classes - 1;
+                atomicAdd(&hn[q * E + kb], 1);
+                if (a.masses) atomicAdd(&hm[q * E + kb], ms[u]);
+            }
+        }
+        if (i1 < np) issue(i1, key, xs, vs, ms);
+    }
+    __syncthreads();
+    const int64_t row = (int64_t)b * C;
+    for (int i = tid; i < C; i += DT) {
+        const int n = hn[i];
+        if (n == 0) continue;
+        atomicAdd(reinterpret_cast<unsigned long long *>(a.number) + row + i, (unsigned long long)n);
+        if (a.masses) atomicAdd(a.mass + row + i, hm[i]);
+    }
+}
+
+template <int KIND>
+void (*decompose_kernel(int coord_f64, int vel_f64))(oa_decomp_args) {
+    return coord_f64 ? (vel_f64 ? k_decompose<KIND, double, double> : k_decompose<KIND, double, float>)
+                     : (vel_f64 ? k_decompose<KIND, float, double> : k_decompose<KIND, float, float>);
+}
+
 uint64_t pow2_at_least(uint64_t v, uint64_t lo) {
     uint64_t c = lo;
     while (c < v) c <<= 1;
@@ -1196,6 +1516,7 @@ int64_t oa_post_struct_size(int32_t which) {
         case 0: return sizeof(oa_collate_args);
         case 1: return sizeof(oa_central_args);
         case 2: return sizeof(oa_mainprog_args);
+        case 3: return sizeof(oa_decomp_args);
         default: return -1;
     }
 }
@@ -1355,6 +1676,50 @@ int oa_main_progenitors(const oa_mainprog_args *args, void *stream) {
         return fail(OA_E_LAUNCH, "oa_main_progenitors: hipFuncSetAttribute");
     hipLaunchKernelGGL(k_mp_tally, dim3(a.n_blocks), dim3(256), (size_t)ts * 8, st, a, hn, ts);
     return check_launch("k_mp_tally");
+}
+
+int oa_decompose(const oa_decomp_args *args, void *stream) {
+    oa_internal_error(nullptr);
+    if (!args) return fail(OA_E_ARG, "oa_decompose: null args");
+    const oa_decomp_args &a = *args;
+    if (a.id_kind < 0 || a.id_kind > 3) return fail(OA_E_ARG, "oa_decompose: id_kind must be 0-3");
+    if (a.n_bins < 1 || a.n_classes < 2 ||
+        (int64_t)a.n_bins * a.n_classes > OA_DECOMP_MAX_CELLS)
+        return fail(OA_E_ARG, "oa_decompose: n_bins >= 1, n_classes >= 2 and n_bins * n_classes "
+                              "<= OA_DECOMP_MAX_CELLS required");
+    if (a.lds_keys < 64 || a.lds_keys > OA_DECOMP_MAX_KEYS || (a.lds_keys & (a.lds_keys - 1)))
+        return fail(OA_E_ARG, "oa_decompose: lds_keys must be a power of two in "
+                              "[64, OA_DECOMP_MAX_KEYS]");
+    if (!a.count || !a.r || !a.vr || !a.number || (a.masses && !a.mass))
+        return fail(OA_E_ARG, "oa_decompose: null output (count, r, vr, number; mass with masses)");
+    if (a.n_box_dims != 0 && a.n_box_dims != 3)
+        return fail(OA_E_ARG, "oa_decompose: n_box_dims must be 0 or 3");
+    if (a.n_blocks < 0 || a.n < 0 || a.n_col < 0)
+        return fail(OA_E_ARG, "oa_decompose: negative n_blocks, n or n_col");
+    if (a.n_blocks == 0) return OA_OK;
+    if (!a.offsets || !a.centres || !a.bulk || !a.radii || !a.col_off || !a.r_edges ||
+        (a.n > 0 && (!a.ids || !a.coords || !a.vels)) || (a.n_col > 0 && (!a.col_keys || !a.col_cnt)))
+        return fail(OA_E_ARG, "oa_decompose: null input pointer");
+    // one work item per (block, run of OA_DECOMP_SHARE particles) pair that can be non-empty
+    const int64_t items = (int64_t)a.n_blocks + a.n / DSHARE + 1;
+    if (items > 0x7FFFFFFFll) return fail(OA_E_ARG, "oa_decompose: n_blocks + n / OA_DECOMP_SHARE >= 2^31");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t cells = (int64_t)a.n_bins * a.n_classes;
+    if (hipMemsetAsync(a.number, 0, (size_t)(a.n_blocks * cells) * 8, st) != hipSuccess ||
+        (a.mass && hipMemsetAsync(a.mass, 0, (size_t)(a.n_blocks * cells) * 8, st) != hipSuccess))
+        return fail(OA_E_LAUNCH, "oa_decompose: hipMemsetAsync");
+    if (a.n == 0) return OA_OK;
+    const int64_t lds = (int64_t)a.lds_keys * (OA_DECOMP_HASH ? 16 : 12) +
+                        ((int64_t)a.n_bins + 1) * 8 + cells * 12;
+    auto k = a.id_kind == OA_ID_I64 ? decompose_kernel<OA_ID_I64>(a.coord_f64, a.vel_f64)
+           : a.id_kind == OA_ID_U64 ? decompose_kernel<OA_ID_U64>(a.coord_f64, a.vel_f64)
+           : a.id_kind == OA_ID_I32 ? decompose_kernel<OA_ID_I32>(a.coord_f64, a.vel_f64)
+                                    : decompose_kernel<OA_ID_U32>(a.coord_f64, a.vel_f64);
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return fail(OA_E_LAUNCH, "oa_decompose: hipFuncSetAttribute");
+    hipLaunchKernelGGL(k, dim3((unsigned)items), dim3(DT), (size_t)lds, st, a);
+    return check_launch("k_decompose");
 }
 
 }  // extern "C"

@@ -24,6 +24,7 @@ import numpy as np
 
 from . import _native as N
 from .utils import myin1d
+from .decomposition import OrbitDecomposition  # noqa: F401  (the example script imports it from here)
 
 
 # ------------------------------------------------------------------ file access

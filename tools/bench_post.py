@@ -1,7 +1,7 @@
 """Benchmarks of SURVEY §8(f) rows f3/f4 on one MI355X (device-resident inputs), each
 with its HBM roofline and the CPU oracle timed on a bounded sample beside it.
 
-  python tools/bench_post.py [--which collate,central,mainprog] [--scale 1.0]
+  python tools/bench_post.py [--which collate,central,mainprog,decompose] [--scale 1.0]
 
 Prints one JSON line per workload:
 * collate  — Apsides.collate_apsides at config-3 scale: 1e4 halos, ~5e6 apsis records
@@ -14,6 +14,11 @@ Prints one JSON line per workload:
 * mainprog — find_main_progenitors: 1e8 int64 halo members in 1e4 halos, 1e4 tracked
              blocks of 100 central IDs; unit = halo members/s; algorithmic bytes = 8 B
              per member + 8 B per tracked ID.
+* decompose — decompose_blocks (orbiting / infalling decomposition): 1e8 float32 particles
+             with int64 IDs in 1e4 blocks, collated slices of ~30 % of each block, 50 bins
+             x 5 classes, scalar mass; unit = particles/s; algorithmic bytes = 8 + 12 + 12
+             read and 12 written per particle + 16 B per collated entry once.  Not in the
+             default --which (it holds ~4.5 GB on the device).
 Timing: HIP events on the launch stream around the device calls only; the kernels'
 share is cross-checked with rocprofv3 --kernel-trace --stats (profiles/).
 """
@@ -215,6 +220,65 @@ def bench_mainprog(scale, cpu_blocks, reps=5):
                              'identical to the GPU: %s' % (n, cpu_blocks, cdt, ok)}}
 
 
+def bench_decompose(scale, cpu_blocks, reps=5):
+    import torch
+    from orbitanalysis_amd.decomposition import BlockDecomposition
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import decomp_oracle as DO
+    rng = np.random.default_rng(8)
+    nh, per = int(1e4 * scale), 10000
+    n = nh * per
+    # IDs: block b holds b * per .. b * per + per - 1 in random order; ~30 % of them collated
+    ids = rng.permuted(np.arange(n, dtype=np.int64).reshape(nh, per), axis=1).ravel()
+    mask = rng.random((nh, per), dtype=np.float32) < 0.3
+    pids = np.flatnonzero(mask.ravel()).astype(np.int64)
+    offsets = np.concatenate([[0], np.cumsum(mask.sum(axis=1))]).astype(np.int64)
+    del mask
+    counts = rng.integers(1, 9, len(pids)).astype(np.int64)
+    centres = rng.uniform(0, 100, (nh, 3)).astype(np.float32).astype(np.float64)
+    x = np.repeat(centres.astype(np.float32), per, axis=0)
+    x += rng.standard_normal((n, 3), dtype=np.float32)
+    x %= np.float32(100)
+    v = rng.standard_normal((n, 3), dtype=np.float32) * np.float32(200)
+    snap = {'ids': ids, 'coordinates': x, 'velocities': v, 'masses': 1.0, 'box_size': 100.0,
+            'region_offsets': np.arange(nh, dtype=np.int64) * per}
+    bulk, radii = np.zeros((nh, 3)), np.full(nh, 1.5)
+    edges = np.linspace(0.0, 2.0, 51)
+    d = BlockDecomposition(snap, centres, bulk, radii, pids, counts, offsets, r_edges=edges,
+                           n_classes=5)
+    d.launch()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        d.launch()
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / reps
+    got = d.result()
+    # CPU: the NumPy restatement on the first cpu_blocks blocks, one core
+    m, mc = cpu_blocks * per, int(offsets[cpu_blocks])
+    sub = dict(snap, ids=ids[:m], coordinates=x[:m], velocities=v[:m],
+               region_offsets=snap['region_offsets'][:cpu_blocks])
+    t0 = time.perf_counter()
+    want = DO.decompose_blocks(sub, centres[:cpu_blocks], bulk[:cpu_blocks], radii[:cpu_blocks],
+                               pids[:mc], counts[:mc], offsets[:cpu_blocks + 1], edges, n_classes=5)
+    cdt = time.perf_counter() - t0
+    ok = np.array_equal(want['counts'], got['counts'][:m]) and \
+        np.array_equal(want['number'], got['number'][:cpu_blocks]) and \
+        np.array_equal(want['radii'], got['radii'][:m])
+    bytes_ = 44.0 * n + 16.0 * len(pids)
+    return {'metric': 'particles/s (decompose_blocks)', 'value': n / (ms * 1e-3),
+            'unit': 'particles/s', 'ms_per_call': ms, 'dtype': 'f32',
+            'config': {'workload': 'decompose: %d particles f32, int64 IDs, %d blocks, %d collated '
+                       'entries, 50 bins x 5 classes, box' % (n, nh, len(pids)),
+                       'lds_keys': int(d.args.lds_keys)},
+            'roofline': dict(roof(bytes_, ms, 'decompose', scale), kernel='k_decompose'),
+            'cpu_baseline': {'value': m / cdt, 'unit': 'particles/s', 'cores': 1, 'kind': 'port',
+                             'sample': '%d of %d blocks, %.1f s; counts, radii and number '
+                             'identical to the GPU: %s' % (cpu_blocks, nh, cdt, ok)}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--which', default='collate,central,mainprog')
@@ -230,6 +294,8 @@ def main():
             r = bench_central(args.scale, 100)
         elif w == 'mainprog':
             r = bench_mainprog(args.scale, 1000)
+        elif w == 'decompose':
+            r = bench_decompose(args.scale, 100)
         else:
             raise SystemExit('unknown workload ' + w)
         log(w, 'done in %.1f s' % (time.time() - t0))
